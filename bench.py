@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Green-Gauss gradient iterations/s on the F6-like dualgrid stand-ins.
 
-    python bench.py --gpus N --steps K --warmup W [--config NAME]
+    python bench.py --gpus N --steps K --warmup W [--config NAME] [--dump-outputs DIR]
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment,
 one rank per GPU), or -- started plainly, without a rank environment -- this process only LAUNCHES: before it
@@ -224,6 +224,32 @@ def launch_ranks(n: int, argv: list, ndev: int, child_cmd=None, timeout: float =
     return rc
 
 
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes in all (every rank together)
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: write the arrays the timed path handed back in its last step as out_dir/<name>.npy (float64), so
+    that two builds run with the same arguments can be compared output for output.  All arrays are indexed by the same
+    row (owned point in the partition's file numbering).  Rows beyond the cap are dropped by a fixed, seeded sample --
+    the same rows in every run of the same arguments -- and the row numbers kept are written as sample_rows.npy.
+    With several ranks every rank writes its own partition's arrays, suffixed _rank<r>, within its share of the cap."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].size * 8 for a in arrays.values())
+    cap = DUMP_CAP_BYTES // max(world, 1)
+    rows = None
+    if n * row_bytes > cap:
+        k = cap // (row_bytes + 8)  # (+8: the row number itself)
+        rows = np.sort(np.random.default_rng(20240901 + rank).choice(n, size=k, replace=False))
+        arrays = dict({name: a[rows] for name, a in arrays.items()}, sample_rows=rows)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print(f"bench.py: wrote {', '.join(f'{name}{suffix}.npy' for name in arrays)} to {out_dir}"
+          + (f" ({len(rows)} of {n} rows, seeded sample)" if rows is not None else f" ({n} rows)"), file=sys.stderr)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -254,7 +280,12 @@ def main() -> None:
                          "ncclSend/ncclRecv issued by the C library; torch: torch.distributed P2P ops; staged: "
                          "through the host (tests)")
     ap.add_argument("--no-strong", action="store_true", help="skip the extra dualgrid.192 strong-scaling measurement at --gpus 8")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (gradients and pseudo flux of the "
+                         "owned points, float64) as DIR/<name>.npy, at most 64 MB in all (a seeded sample of rows beyond)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from __graft_entry__ import load_package
     pkg = load_package()  # (the C host library only: nothing here touches the GPU)
@@ -305,8 +336,9 @@ def main() -> None:
         walls[key] = round(walls.get(key, 0.0) + now - since, 2)
         return now
 
-    def measure(cfg: dict, keep_solver: bool = False):
-        """set-up, W untimed + exactly K timed steps (max over ranks), exchange check, overlap report"""
+    def measure(cfg: dict, keep_solver: bool = False, dump: bool = False):
+        """set-up, W untimed + exactly K timed steps (max over ranks), exchange check, overlap report; dump: the outputs
+        of the last timed step go to --dump-outputs"""
         dims, ndom = cfg["dims"], cfg["ndomains"]
         gp = pkg.gen_params(*dims, ndomains=ndom)
         tag = cfg["name"]
@@ -420,6 +452,8 @@ def main() -> None:
                 solver.run_steps(max(args.warmup, 1), with_exchange=True, overlap=True)
             dt_cold = timed(args.steps, conditioned=False, with_exchange=True, overlap=True)
             dt = timed(args.steps, with_exchange=True, overlap=True)
+            if dump:  # (before the exchange check: its steps run in a scaled field)
+                outputs = {"grad": solver.grad_host()[:nown].copy(), "psd_flux": part.psd_flux[:nown].copy()}
             if world == 1:
                 break
             chk = exchange_check()
@@ -431,6 +465,8 @@ def main() -> None:
             if not solver.fallback():
                 break
         tl = lap(f"{tag}: warm-up, timed steps, exchange check", tl)
+        if dump:
+            dump_outputs(args.dump_outputs, outputs, rank, world)
         its = args.steps / dt  # iterations/s of the whole mesh
         mesh_points = dims[0] * dims[1] * dims[2]
         res = {
@@ -486,7 +522,7 @@ def main() -> None:
     # fewer ranks: the 8-rank command cannot be rehearsed on a box that admits 6 GPU processes)
     role = mg.bench_role(world)
     cfg = mg.bench_config(args.config or mg.default_bench_config(role), world)
-    res, solver, part = measure(cfg, keep_solver=True)
+    res, solver, part = measure(cfg, keep_solver=True, dump=bool(args.dump_outputs))
     nfaces_part, nown, nadd = part.nfaces, part.nown, part.nall - part.nown
 
     out = {

@@ -400,3 +400,68 @@ esac
     monkeypatch.setenv("PATH", f"{tmp_path}:{os.environ['PATH']}")
     pw = bench.power_beside(lambda: None, seconds=0.3)
     assert pw["socket_power_w"] == 1388.0 and pw["shader_clock_mhz"] == 2029 and pw["power_cap_w"] == 1400.0 and pw["samples"] >= 1, pw
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: whole arrays when they fit; beyond the cap the same seeded sample of rows in every run, the row
+    numbers beside them, and nothing over the cap"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(1)
+    arrays = {"grad": rng.standard_normal((1000, 7, 3)), "psd_flux": rng.standard_normal((1000, 3))}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["grad.npy", "psd_flux.npy"]
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 100 * (168 + 24 + 8) + 50)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_CAP_BYTES + 3 * 128  # (+ .npy headers)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and rows.dtype == np.float64
+    for name in ("grad", "psd_flux", "sample_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.npy"), arrays["grad"][rows.astype(np.int64)])
+    # several ranks: each its own files, in its share of the cap
+    bench.dump_outputs(str(tmp_path / "r"), arrays, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "r")) == ["grad_rank1.npy", "psd_flux_rank1.npy", "sample_rows_rank1.npy"]
+    assert len(np.load(tmp_path / "r" / "sample_rows_rank1.npy")) == 50
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_what_the_timed_steps_computed(gpu, orc, tmp_path):
+    """bench.py --dump-outputs DIR: the gradients and pseudo flux of the last timed step on the headline partition, against
+    the oracle on the same partition; a second run with the same arguments writes the same arrays bit for bit"""
+    import numpy as np
+    from conftest import TOL, rel_err
+    from cfd_proxy_amd import multigpu as mg
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--no-finest",
+                            "--no-irregular", "--no-loopback", "--no-power", "--no-cpu", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 7
+    assert sorted(os.listdir(dirs[0])) == ["grad.npy", "psd_flux.npy"]
+    assert sum(f.stat().st_size for f in dirs[0].iterdir()) <= 64 << 20
+    for name in ("grad", "psd_flux"):
+        a, b = np.load(dirs[0] / f"{name}.npy"), np.load(dirs[1] / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    cfg = mg.bench_config("dualgrid.12", 1)
+    part, _ = mg.build_rank_partition(gpu.gen_params(*cfg["dims"], ndomains=cfg["ndomains"]), cfg["ndomains"], 1, 0)
+    nown = part.nown
+    grad, flux = np.load(dirs[0] / "grad.npy"), np.load(dirs[0] / "psd_flux.npy")
+    assert grad.shape == (nown, 7, 3) and flux.shape == (nown, 3)
+    ref = orc.CpuRef(part.fpoint, part.fnormal, part.pvolume, nown, nthreads=4)
+    g_ref = ref.gradients(part.var.copy())
+    f_ref = ref.flux(g_ref, mode=0)
+    ref.close()
+    got = g_ref.copy()
+    got[:nown] = grad
+    assert rel_err(orc, got, g_ref, part.fpoint, part.fnormal, part.pvolume, part.var, nown) <= TOL
+    assert np.abs(flux - f_ref[:nown]).max() <= TOL * np.abs(f_ref[:nown]).max()
+    part.free()

@@ -1,6 +1,8 @@
 """Sanitizer builds of the C host side, on the CPU (the GPU pool offers none): AddressSanitizer + UBSan over the
 loader / generator / merger / tiler, ThreadSanitizer over the call election."""
 import os
+import platform
+import shutil
 import subprocess
 import sys
 
@@ -14,6 +16,15 @@ PKG = os.path.join(ROOT, "cfd-proxy_amd")
 def _gcc_lib(name):
     p = subprocess.run(["gcc", "-print-file-name=" + name], capture_output=True, text=True).stdout.strip()
     return p if os.path.isabs(p) and os.path.exists(p) else None
+
+
+def _without_aslr(cmd):
+    """this gcc's ThreadSanitizer expects the program and its libraries inside fixed address ranges, which a kernel that
+    randomises with more bits (vm.mmap_rnd_bits = 32) can place them outside of ("FATAL: ThreadSanitizer: unexpected
+    memory mapping", before main()): the test host runs with address-space randomisation off for that one process
+    (setarch -R sets a personality flag of the child; nothing system-wide changes)"""
+    setarch = shutil.which("setarch")
+    return [setarch, platform.machine(), "-R", *cmd] if setarch else list(cmd)
 
 
 @pytest.mark.skipif(_gcc_lib("libtsan.so") is None, reason="no libtsan in this image")
@@ -33,8 +44,8 @@ def test_call_election_under_thread_sanitizer(pkg, scenario, env, want):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     e = {k: v for k, v in os.environ.items() if k != "CFDP_CALL_MODE"}
     e.update(env, TSAN_OPTIONS="halt_on_error=1 exitcode=66 suppressions=" + os.path.join(ROOT, "tests", "tsan.supp"))
-    r = subprocess.run([os.path.join(PKG, "build", "tsan", "host_call_election"), scenario], capture_output=True, text=True,
-                       timeout=300, env=e)
+    r = subprocess.run(_without_aslr([os.path.join(PKG, "build", "tsan", "host_call_election"), scenario]), capture_output=True,
+                       text=True, timeout=300, env=e)
     assert "ThreadSanitizer" not in r.stderr and r.returncode != 66, r.stderr[-3000:]
     if want:
         assert r.returncode == 0 and want in r.stdout, r.stdout + r.stderr[-1500:]
