@@ -290,6 +290,12 @@ def _declare_hip(lib: C.CDLL) -> None:
     lib.cfdp_gpu_time_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]
     lib.cfdp_gpu_vcycle.argtypes = [P(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]
     lib.cfdp_gpu_counts.argtypes = [vp, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.cfdp_gpu_set_grad_adjoint.argtypes = [vp, P(C.c_double)]
+    lib.cfdp_gpu_get_var_adjoint.argtypes = [vp, P(C.c_double)]
+    lib.cfdp_gpu_gradients_adjoint.argtypes = [vp, vp]
+    lib.cfdp_gpu_adjoint_group.argtypes = [P(vp), C.c_int, C.c_int]
+    lib.cfdp_gpu_step_adjoint_rccl.argtypes = [vp, C.c_int]
+    lib.cfdp_gpu_adjoint_ptrs.argtypes = [vp, P(vp), P(vp)]
 
 
 def host_lib() -> C.CDLL:
@@ -651,6 +657,13 @@ def algo_bytes_flux(nfaces: int, nown: int, nadd: int) -> float:
     return host_lib().cfdp_algo_bytes_flux(nfaces, nown, nadd)
 
 
+def algo_bytes_adjoint(nfaces: int, nown: int, nadd: int) -> float:
+    """compulsory bytes of one adjoint pass, counted as algo_bytes_grad counts the gradient's: every face's normal and
+    end points once (32), every owned point's gbar row and volume read and its vbar row written (168 + 8 + 56), every
+    ghost's gbar row and volume read (168 + 8)"""
+    return 32.0 * nfaces + 232.0 * nown + 176.0 * nadd
+
+
 # ----------------------------------------------------------------------------------- Plan
 class Plan:
     """The GPU tiling of one partition (host/tiling.c) -- the init_threads() analogue."""
@@ -742,6 +755,7 @@ class GpuPartition:
             # (lanes first: the upload refuses tiles whose points x lanes exceed a workgroup)
             self._ck(self.lib.cfdp_gpu_set_variant(self.h, grad_lanes, flux_lanes))
             self._ck(self.lib.cfdp_gpu_upload_plan(self.h, plan.ptr))
+            self._new2old = plan.new2old.copy()  # device numbering -> file numbering (the torch op renumbers with it)
         finally:
             plan.free()
         self.push_fields()
@@ -977,6 +991,40 @@ class GpuPartition:
         self._ck(self.lib.cfdp_gpu_scaled_check_end(self.h, C.byref(r)))
         return {k: getattr(r, k) for k, _ in ScaledCheck._fields_}
 
+    # ---- the adjoint of the gradient, gbar -> vbar (cfdproxy_hip.h: cfdp_gpu_*_adjoint)
+    def set_grad_adjoint(self, gbar: np.ndarray) -> None:
+        """gbar [nall][7][3] in file numbering; the owned rows are read"""
+        g = np.ascontiguousarray(gbar, np.float64)
+        if g.shape != (self.dom.nall, NGRAD, 3):
+            raise ValueError(f"gbar must be [{self.dom.nall}][{NGRAD}][3], not {list(g.shape)}")
+        self._ck(self.lib.cfdp_gpu_set_grad_adjoint(self.h, self._dp(g)))
+
+    def gradients_adjoint(self, stream: int = 0) -> None:
+        """one adjoint pass, ghost points' gbar taken as 0 (the transpose of this partition's own map)"""
+        self._ck(self.lib.cfdp_gpu_gradients_adjoint(self.h, C.c_void_p(stream)))
+
+    def get_var_adjoint(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """vbar [nall][7] in file numbering: owned rows written, ghost rows left as they are in `out` (zeros if none given)"""
+        v = np.zeros((self.dom.nall, NGRAD)) if out is None else out
+        if v.shape != (self.dom.nall, NGRAD) or v.dtype != np.float64 or not v.flags.c_contiguous:
+            raise ValueError(f"vbar must be a contiguous float64 [{self.dom.nall}][{NGRAD}] array")
+        self._ck(self.lib.cfdp_gpu_get_var_adjoint(self.h, self._dp(v)))
+        return v
+
+    def step_adjoint_rccl(self, with_exchange: bool = True) -> None:
+        """gather + ncclSend / ncclRecv of the gbar rows + the adjoint pass (the context's own RCCL communicator)"""
+        self._ck(self.lib.cfdp_gpu_step_adjoint_rccl(self.h, int(with_exchange)))
+
+    def adjoint_ptrs(self):
+        """(gbar [nall][21], vbar [nown][7]): the context's device buffers, device (tile) numbering"""
+        gb, vb = C.c_void_p(), C.c_void_p()
+        self._ck(self.lib.cfdp_gpu_adjoint_ptrs(self.h, C.byref(gb), C.byref(vb)))
+        return gb.value or 0, vb.value or 0
+
+    def new2old(self) -> np.ndarray:
+        """[nall]: device (tile) numbering -> file numbering of the uploaded plan"""
+        return self._new2old
+
     def close(self) -> None:
         if self.h:
             self.lib.cfdp_gpu_destroy(self.h)
@@ -990,6 +1038,16 @@ def group_iteration(parts: Sequence[GpuPartition], with_exchange=True, overlap=T
     arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
     rc = lib.cfdp_gpu_iteration_group(arr, len(parts), int(with_exchange), int(overlap), int(with_flux), flux_mode)
     if rc:
+        raise GpuError(lib.cfdp_gpu_last_error().decode())
+
+
+def group_adjoint(parts: Sequence[GpuPartition], with_exchange: bool = True) -> None:
+    """One adjoint pass of G in-process ranks: with_exchange -- every rank's gbar rows of its send points go into its
+    partners' ghost rows first (peer copies; the forward exchange), so the result is the transpose of the GLOBAL operator
+    on every owned point; without -- each partition's own transpose (ghost gbar taken as 0)"""
+    lib = hip_lib()
+    arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
+    if lib.cfdp_gpu_adjoint_group(arr, len(parts), int(with_exchange)):
         raise GpuError(lib.cfdp_gpu_last_error().decode())
 
 

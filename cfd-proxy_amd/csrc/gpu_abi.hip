@@ -88,6 +88,7 @@ int cfdp_gpu_create(int device, cfdp_gpu **out) {
 
 static void free_device(cfdp_gpu *g) {
   g->drop_graphs();
+  adjoint_release(g);
   (void)hipFree(g->d_tiles); (void)hipFree(g->d_blob); (void)hipFree(g->d_halo); (void)hipFree(g->d_sendidx); (void)hipFree(g->d_rowlist);
   (void)hipFree(g->d_var); (void)hipFree(g->d_flux);
   (void)hipFree(g->sc.d_state); (void)hipFree(g->sc.d_fref); (void)hipFree(g->sc.d_skip); (void)hipFree(g->sc.d_var0);

@@ -285,6 +285,15 @@ struct cfdp_gpu {
       }
     }
   }
+  // adjoint of the gradient (csrc/gpu_adjoint.hip): device buffers allocated by the first adjoint entry point used, in
+  // device numbering -- gbar [nall][21] plain rows (owned, then ghost rows in message order: the exchange lands in the
+  // ghost block as it does for grad), vbar [nown][7], ivol [nall] (1/V; ghost rows the owner's, once exchanged),
+  // the send arena [nsend][21]
+  struct adjoint_state {
+    double *d_gbar = nullptr, *d_vbar = nullptr, *d_ivol = nullptr, *d_send = nullptr;
+    bool ghost_ivol = false;                // the ghost rows of d_ivol hold the owners' 1/V
+    hipEvent_t ev_sent = nullptr, ev_done = nullptr;
+  } adj;
   gg_args args() const {
     gg_args a;
     a.tiles = d_tiles; a.blob = d_blob; a.halo_idx = d_halo; a.rowlist = d_rowlist; a.rowlist_stride = rowlist_stride; a.var = d_var;
@@ -318,7 +327,12 @@ __attribute__((visibility("hidden"))) int launch_flux_tiles(cfdp_gpu *g, int mod
 int launch_flux(cfdp_gpu *g, int mode, hipStream_t st, const gg_push_args *wait = nullptr);
 int launch_fused(cfdp_gpu *g, int which, hipStream_t st, const gg_push_args *push = nullptr);
 void fused_done(cfdp_gpu *g);
+// gpu_adjoint.hip
+void adjoint_release(cfdp_gpu *g);  // frees the adjoint buffers (with the plan)
 // gpu_exchange.hip
+// one grouped ncclSend / ncclRecv per partner slot on stream st: rows [send_off[s], send_off[s+1]) of `send` to partner s,
+// rows [recv_off[s], recv_off[s+1]) of `recv` from it, `rowlen` doubles per row (the context's communicator)
+int rccl_exchange_rows(cfdp_gpu *g, const double *send, double *recv, int rowlen, hipStream_t st);
 void ipc_release(cfdp_gpu *g);
 void ipc_push_args(cfdp_gpu *g, int parity, gg_push_args *out);
 long ipc_max_polls();

@@ -141,6 +141,26 @@ int enqueue_exchange(cfdp_gpu *g) {
   return 0;
 }
 
+}  // namespace
+
+// the same messages for another per-point field (the adjoint's gbar rows and volumes: csrc/gpu_adjoint.hip)
+extern "C++" int cfdp_detail::rccl_exchange_rows(cfdp_gpu *g, const double *send, double *recv, int rowlen, hipStream_t st) {
+  if (!g->comm) return fail("no communicator: call cfdp_gpu_rccl_init()");
+  if (g->comm_nranks == 1 && !g->partner.empty() && !g->rccl_self_exchange)
+    return fail("the communicator has ONE rank: this exchange would send every partner's rows to the rank itself (for loopback "
+                "measurements say so first: cfdp_gpu_rccl_allow_self_exchange)");
+  RCCL_TRY(rccl.GroupStart());
+  for (size_t s = 0; s < g->partner.size(); s++) {
+    size_t sn = (size_t)(g->send_off[s + 1] - g->send_off[s]) * rowlen, rn = (size_t)(g->recv_off[s + 1] - g->recv_off[s]) * rowlen;
+    if (g->comm_nranks == 1 && g->rccl_self_exchange) sn = rn = sn < rn ? sn : rn;  // (measurement / plumbing only, as above)
+    if (sn) RCCL_TRY(rccl.Send(send + (size_t)g->send_off[s] * rowlen, sn, ncclDouble, g->peer[s], g->comm, st));
+    if (rn) RCCL_TRY(rccl.Recv(recv + (size_t)g->recv_off[s] * rowlen, rn, ncclDouble, g->peer[s], g->comm, st));
+  }
+  RCCL_TRY(rccl.GroupEnd());
+  return 0;
+}
+
+namespace {
 int one_step(cfdp_gpu *g, int with_exchange, int overlap, int with_flux, int flux_mode) {
   if (cfdp_gpu_step_pre(g, with_exchange, overlap)) return 1;
   if (g->pending_exchange && enqueue_exchange(g)) return 1;

@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import (FLUX_CONSISTENT, TILES_ALL, TILES_BOUNDARY, TILES_INTERIOR, VAR_HASH, Domain,
-               GpuPartition, fill_var, gen_domain, gen_global_ids, load_domain, merge_domains,
+               GpuError, GpuPartition, fill_var, gen_domain, gen_global_ids, load_domain, merge_domains,
                merge_requests, merge_set_send, rank_domain_list)
 
 ROWLEN = 21  # NGRAD * 3 doubles per halo point (reference dim2, src/gradients.c:176-177)
@@ -694,6 +694,17 @@ class RankSolver:
             return
         for _ in range(steps):
             self.step(with_exchange, overlap, with_flux, flux_mode)
+
+    def step_adjoint(self, with_exchange: bool = True) -> None:
+        """one pass of the gradient's adjoint, gbar -> vbar (gbar set with self.gpu.set_grad_adjoint, vbar read with
+        self.gpu.get_var_adjoint): with the exchange, the gbar rows of the send points travel to the partners first over the
+        library's own RCCL communicator (cfdp_gpu_step_adjoint_rccl) and the result is the transpose of the global operator.
+        Only the "rccl" transport carries it: the library refuses the xGMI write + notify transport for the adjoint, and no
+        other transport is put in its place"""
+        comm = with_exchange and self.world > 1 and bool(self.partners)
+        if comm and self.transport != "rccl":
+            raise GpuError(f"the adjoint exchange runs over the library's RCCL communicator only (transport is {self.transport!r})")
+        self.gpu.step_adjoint_rccl(comm)
 
     def synchronize(self) -> None:
         self.gpu.sync()  # also runs a flux deferred by the fused mode

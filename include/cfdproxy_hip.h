@@ -343,6 +343,34 @@ int  cfdp_gpu_refresh_graphs(cfdp_gpu *g);
 int  cfdp_gpu_vcycle(cfdp_gpu **levels, int nlevels, int sweeps, int cycles, int flux_mode,
                      int use_graph, float *ms_per_cycle);
 
+/* Adjoint (transpose) of the Green-Gauss gradient: gbar -> vbar, for sensitivities (a discrete adjoint) and for
+ * differentiating the gradient (a reverse-mode autograd op).  With s[p] = gbar[p] / V_p, for every owned point q
+ *     vbar[q][e] = sum over the faces f of q of  sigma_{f,q} * 1/2 n_f . (s[q][e] - s[r_f][e])
+ * (r_f = the other end of f, sigma = +1 where q is p0 of the face, -1 where it is p1).  A ghost point's s is 0 (the transpose
+ * of the partition's own map var_own -> grad_own, ghost var held constant; also the adjoint of an unpartitioned mesh) or,
+ * with_exchange = 1, its owner's s: the transpose of the global operator.  The halo path is the FORWARD exchange of raw
+ * 21-double gbar rows over the send / receive lists of the gradient (a ghost's 1/V is its owner's, sent once the same way):
+ * every face of an owned point lies in that point's partition, so no accumulating exchange is needed.  A point without
+ * faces gets vbar = 0; ghost rows of vbar are never written.  The buffers (gbar own + ghost rows, vbar, 1/V) belong to the
+ * context, allocated by the first adjoint call, freed with the plan.  The face loop: csrc/gg_adjoint.hip.
+ *   cfdp_gpu_set_grad_adjoint   gbar [nall][7][3], FILE numbering; the owned rows are read
+ *   cfdp_gpu_get_var_adjoint    vbar [nall][7], FILE numbering; owned rows written, ghost rows untouched (syncs the device)
+ *   cfdp_gpu_gradients_adjoint  one adjoint pass on `stream` (NULL: the context's main stream), with_exchange = 0 semantics
+ *   cfdp_gpu_adjoint_group      G in-process ranks (peer copies into the partners' ghost rows), then every rank's pass
+ *   cfdp_gpu_step_adjoint_rccl  one rank per process: gather + grouped ncclSend / ncclRecv + the pass, in the order of the
+ *                               main stream (cfdp_gpu_rccl_init first when with_exchange and the partition has partners)
+ *   cfdp_gpu_adjoint_ptrs       the device buffers in DEVICE (tile) numbering: gbar [nall][21] plain rows (owned rows, then
+ *                               ghost rows in message order), vbar [nown][7] -- for a caller that fills / reads them itself
+ *                               (the torch op, cfd-proxy_amd/autograd.py)
+ * A context with the xGMI write + notify transport switched on (cfdp_gpu_ipc_ready / _enable) is refused by the group and
+ * step calls with a message: the adjoint has no exchange over that transport, and none is substituted for it.          */
+int  cfdp_gpu_set_grad_adjoint(cfdp_gpu *g, const double *gbar);
+int  cfdp_gpu_get_var_adjoint(cfdp_gpu *g, double *vbar);
+int  cfdp_gpu_gradients_adjoint(cfdp_gpu *g, void *stream);
+int  cfdp_gpu_adjoint_group(cfdp_gpu **ranks, int G, int with_exchange);
+int  cfdp_gpu_step_adjoint_rccl(cfdp_gpu *g, int with_exchange);
+int  cfdp_gpu_adjoint_ptrs(cfdp_gpu *g, void **dev_gbar, void **dev_vbar);
+
 /* sizes for callers that allocate */
 int  cfdp_gpu_counts(const cfdp_gpu *g, int *nown, int *nall, int *nsend, int *nrecv);
 
